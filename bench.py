@@ -11,12 +11,15 @@ every raster sample from the picture's planes and the sub-carrier, filters it,
 adds the sound carriers and NICAM and stores the int16 I/Q. The block's side
 inputs (sound-carrier stream, NICAM symbols, the test card's picture planes) are
 staged into HBM before the clock starts; every step renders all F frames again.
-Before any number is taken EVERY sample of the block is compared with the
-unmodified reference CLI run in the same job (and with its committed digest).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--full]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--full] [--dump-outputs DIR]
 
-N = 1            one process, one engine, no torch (HIP through libhvk only).
+N = 1            one process, one engine, no torch (HIP through libhvk only). A plain run
+                 stages, warms up, times the K steps and prints the line; --dump-outputs
+                 writes what the last timed step rendered. --full first compares EVERY
+                 sample of the block with the unmodified reference CLI run in the same job
+                 (and with its committed digest), and after the headline adds the sections
+                 below and the CPU baseline.
 N > 1, as typed  one process drives an engine per device through hvk_group_* (C inside
                  libhvk): blocks dealt round-robin, a step = every engine's launch + the
                  gather of the round onto the root device (RCCL between distinct devices).
@@ -26,9 +29,9 @@ N > 1, torchrun  (WORLD_SIZE = N: what the driver launches) one rank per GPU, bl
                  barrier + synchronize either side, maximum over ranks (tools/bench_multi.py).
 
 stdout carries ONE line, the last thing printed: a compact JSON object (< 4 KB) with the
-contract's keys plus "roofline" and "cpu_baseline". Everything else -- the other BASELINE
-configurations, moving pictures, SECAM, the drop-in binary, the one-hour run (--full) --
-goes to the sidecar bench_detail.json (--detail-out) and to stderr.
+contract's keys (with --full plus "parity_gate", "roofline" and "cpu_baseline"). Everything
+else -- with --full the other BASELINE configurations, moving pictures, SECAM, the drop-in
+binary, the one-hour run -- goes to the sidecar bench_detail.json (--detail-out) and to stderr.
 """
 import argparse
 import ctypes
@@ -221,9 +224,30 @@ def device_sync():
     hip.hipDeviceSynchronize()
 
 
+DUMP_SEED = 20240601        # --dump-outputs: the seed of the sampled positions (fixed: two builds dump the same positions)
+DUMP_SAMPLES = 1 << 21      # --dump-outputs: sampled IQ pairs of the block (2 x 16 MB with their positions, + 5 MB for frame 0)
+
+
+def dump_outputs(iq, frame_samples, out_dir, log):
+    """What the timed path handed over in its last step -- the block's int16 I/Q pairs, (F * frame_samples, 2) -- as float32
+    .npy files under out_dir: iq_frame0 (the block's first frame, whole), iq_sample (a fixed, seeded sample of positions
+    over the whole block) and iq_sample_index (those positions, float64). About 39 MB for the default block."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = iq.shape[0]
+    idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=min(n, DUMP_SAMPLES)))
+    arrays = {"iq_frame0": iq[:frame_samples].astype(np.float32),
+              "iq_sample": iq[idx].astype(np.float32),
+              "iq_sample_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs: %s (%s)" % (out_dir, ", ".join("%s %s" % (k, "x".join(map(str, v.shape))) for k, v in arrays.items())))
+
+
 def headline_one(args, log):
-    """N = 1: one engine on one device. Returns the result dict (every key; compact_line() picks)."""
-    import numpy as np   # noqa: F401
+    """N = 1: one engine on one device. Returns the result dict (every key; compact_line() picks).
+    A plain run sets up, warms up, times the steps (and dumps their output with --dump-outputs); --full adds the
+    parity gate, the kernel's own time, the spread, a fresh block end to end, the other configurations and the CPU baseline."""
     import hacktv_amd as H
     import util
 
@@ -242,25 +266,7 @@ def headline_one(args, log):
     t_stage = time.perf_counter() - t0
     log("staged %d frames (host control path + H2D) in %.2f s = %.1f Msamples/s" % (F, t_stage, F * FS / t_stage / 1e6))
 
-    # ---- parity gate before any number: EVERY sample of the block against the unmodified reference ----
-    e.launch()
-    e.sync()
-    cli = ["--filter"] + (["--noaudio"] if args.noaudio else [])
-    got = hashlib.sha256(e.fetch(0, F * FS).tobytes()).hexdigest()
-    want, how = ref_stream_sha(MODE, SAMPLE_RATE, cli, 0, F, FS * 4), None
-    if want is not None:
-        how = "hacktv_ref run in this job"
-        if got != want:
-            raise SystemExit("parity gate failed: frames 0..%d differ from the reference CLI's output" % (F - 1))
-    com = None if args.noaudio else committed_digest(F)
-    if com is not None:
-        if got != com:
-            raise SystemExit("parity gate failed: the first %d frames differ from the committed reference digest" % F)
-        how = (how + " + committed digest") if how else "committed digest"
-    if how is None:
-        raise SystemExit("parity gate: neither oracle/_ref/hacktv_ref nor a committed digest for %d frames -- refusing to report a number" % F)
-    gate = "all %d frames x %d samples sha256 == %s" % (F, FS, how)
-    log("parity gate ok: " + gate)
+    gate = parity_gate_one(e, args, F, FS, log) if args.full else None
 
     # ---- warm-up, then --settle seconds of the same launches untimed (sustained clocks), then the timed region ----
     for _ in range(args.warmup):
@@ -279,6 +285,63 @@ def headline_one(args, log):
     e.sync()
     device_sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(e.fetch(0, F * FS), FS, args.dump_outputs, log)
+
+    samples = F * FS
+    value = samples * args.steps / dt / 1e6
+    ms_per_step = dt / args.steps * 1e3
+    res = {
+        "metric": METRIC, "value": round(value, 1), "unit": "Msamples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "int16 data, int32 accumulate",
+        "data": "synthetic: built-in test card + 1 kHz tone (hacktv test source); every step renders all frames of the staged block again; "
+                "side inputs and the card's picture planes resident in HBM (made once, outside the clock)",
+        "config": {"workload": "-m i -s 16000000 --filter test%s (PAL-I AM-VSB + 51-tap FIR, FM mono + NICAM)" % (" --noaudio" if args.noaudio else ""),
+                   "frames_per_gpu_per_step": F, "samples_per_step": samples, "parallelism": "one engine on one GPU"},
+        "settle": {"seconds": args.settle, "untimed_steps": settle_steps},
+        "host_prepass": {"stage_s": round(t_stage, 3), "Msamples_per_s": round(F * FS / t_stage / 1e6, 1),
+                         "note": "staging one block before the clock: the host's serial sound chains (one core) + H2D of the side streams"},
+        "also": {"stage_with_sound_Msamples_per_s": round(F * FS / t_stage / 1e6, 1)},
+    }
+    log("value %.1f Msamples/s, %.4f ms per step" % (value, ms_per_step))
+    if args.full:
+        res["parity_gate"] = gate
+        full_one(e, g, H, args, res, log)
+    e.close()
+    return res
+
+
+def parity_gate_one(e, args, F, FS, log):
+    """--full, before any number: EVERY sample of the block against the unmodified reference CLI run now and against the
+    committed digest."""
+    e.launch()
+    e.sync()
+    cli = ["--filter"] + (["--noaudio"] if args.noaudio else [])
+    got = hashlib.sha256(e.fetch(0, F * FS).tobytes()).hexdigest()
+    want, how = ref_stream_sha(MODE, SAMPLE_RATE, cli, 0, F, FS * 4), None
+    if want is not None:
+        how = "hacktv_ref run in this job"
+        if got != want:
+            raise SystemExit("parity gate failed: frames 0..%d differ from the reference CLI's output" % (F - 1))
+    com = None if args.noaudio else committed_digest(F)
+    if com is not None:
+        if got != com:
+            raise SystemExit("parity gate failed: the first %d frames differ from the committed reference digest" % F)
+        how = (how + " + committed digest") if how else "committed digest"
+    if how is None:
+        raise SystemExit("parity gate: neither oracle/_ref/hacktv_ref nor a committed digest for %d frames -- refusing to report a number" % F)
+    gate = "all %d frames x %d samples sha256 == %s" % (F, FS, how)
+    log("parity gate ok: " + gate)
+    return gate
+
+
+def full_one(e, g, H, args, res, log):
+    """--full at N = 1, after the headline: the kernel's own time (the roofline object), the spread, one fresh block end
+    to end, the other BASELINE configurations, the minutes-long sections (unless --no-deep) and the CPU baseline."""
+    F = args.frames
+    FS = e.info["frame_samples"]
+    samples = F * FS
 
     # the kernel's own time, for the roofline object: the same steps once more with HIP events recorded around every
     # launch on the launch stream (recording costs a little: not inside the region `value` comes from)
@@ -303,31 +366,13 @@ def headline_one(args, log):
     sub.sort()
 
     names = e.kernel_names()
-    samples = F * FS
-    value = samples * args.steps / dt / 1e6
-    ms_per_step = dt / args.steps * 1e3
     roof = hbm_roofline(names[-1], kern_ms, n_k, samples, traffic_per_launch(F))
-    roof["path_frac"] = round(BYTES_PER_SAMPLE * samples / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+    roof["path_frac"] = round(BYTES_PER_SAMPLE * res["value"] * 1e6 / 1e9 / HBM_PEAK_GBS, 4)
     if len(names) > 1:
         roof["other_kernel"] = {"kernel": names[0], "avg_launch_ms": round(raster_ms, 4), "launches_timed": int(n_r)}
-    res = {
-        "metric": METRIC, "value": round(value, 1), "unit": "Msamples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "int16 data, int32 accumulate",
-        "data": "synthetic: built-in test card + 1 kHz tone (hacktv test source); every step renders all frames of the staged block again; "
-                "side inputs and the card's picture planes resident in HBM (made once, outside the clock)",
-        "config": {"workload": "-m i -s 16000000 --filter test%s (PAL-I AM-VSB + 51-tap FIR, FM mono + NICAM)" % (" --noaudio" if args.noaudio else ""),
-                   "frames_per_gpu_per_step": F, "samples_per_step": samples, "parallelism": "one engine on one GPU"},
-        "parity_gate": gate,
-        "roofline": roof,
-        "ms_per_step_min": round(sub[0], 4), "ms_per_step_median": round(sub[len(sub) // 2], 4),
-        "settle": {"seconds": args.settle, "untimed_steps": settle_steps},
-        "host_prepass": {"stage_s": round(t_stage, 3), "Msamples_per_s": round(F * FS / t_stage / 1e6, 1),
-                         "note": "staging one block before the clock: the host's serial sound chains (one core) + H2D of the side streams"},
-        "also": {"stage_with_sound_Msamples_per_s": round(F * FS / t_stage / 1e6, 1)},
-    }
-    log("value %.1f Msamples/s, %.4f ms per step; %s %.4f ms per launch = %.4f of the HBM roofline" %
-        (value, ms_per_step, names[-1], kern_ms, roof["frac"]))
+    res["roofline"] = roof
+    res["ms_per_step_min"], res["ms_per_step_median"] = round(sub[0], 4), round(sub[len(sub) // 2], 4)
+    log("%s %.4f ms per launch = %.4f of the HBM roofline" % (names[-1], kern_ms, roof["frac"]))
 
     # ---- one FRESH block end to end (the PCIe-inclusive rate, never `value`) ----
     host_out = e.host_buffer(F * FS)
@@ -350,16 +395,14 @@ def headline_one(args, log):
     e.close()
 
     # ---- the other BASELINE configurations, briefly (each gated against the reference CLI run in this job) ----
+    import bench_sections as S
     if not args.no_configs:
-        import bench_sections as S
         S.quick_sections(H, g, args, res, log)
-    if args.full:
-        import bench_sections as S
+    if not args.no_deep:
         S.full_sections(H, g, args, res, log)
     if not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(log)
         log("cpu_baseline: %s %s (%s)" % (res["cpu_baseline"]["value"], res["cpu_baseline"]["unit"], res["cpu_baseline"]["kind"]))
-    return res
 
 
 def parse_args(argv=None):
@@ -370,9 +413,14 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=128, help="frames per GPU per step")
     ap.add_argument("--device", type=int, default=0, help="N = 1: the HIP device")
     ap.add_argument("--devices", default=None, help="N > 1 as typed: one HIP device ordinal per engine, e.g. 0,0 (default 0..N-1)")
-    ap.add_argument("--full", action="store_true", help="also: moving pictures, SECAM, the drop-in binary, the C group at N = 1, the one-hour run (minutes)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the brief sections for BASELINE configs 1, 3, 4 and --noaudio")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="N = 1: after the headline also the parity gate against the reference, the "
+                    "roofline, the other BASELINE configurations, moving pictures, SECAM, the drop-in binary, the C group, the one-hour "
+                    "run and the CPU baseline (minutes)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the brief sections for BASELINE configs 1, 3, 4 and --noaudio")
+    ap.add_argument("--no-deep", action="store_true", help="--full: skip the minutes-long sections (moving pictures, SECAM, drop-in, C group, one hour)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="N = 1: write what the last timed step rendered to DIR/*.npy "
+                    "(float32: frame 0 of the block whole, a fixed seeded sample of the block, the sample's positions)")
     ap.add_argument("--noaudio", action="store_true", help="render the --noaudio variant instead (not the metric configuration)")
     ap.add_argument("--settle", type=float, default=0.6, help="seconds of untimed launches before the clock starts (sustained clocks)")
     ap.add_argument("--detail-out", default=os.path.join(ROOT, "bench_detail.json"), help="sidecar with every section ('' = none)")
@@ -394,6 +442,8 @@ def main(argv=None):
         if rank == 0:
             print("[bench] " + msg, file=sys.stderr, flush=True)
 
+    if args.dump_outputs and (world > 1 or args.gpus > 1 or args.devices):
+        raise SystemExit("--dump-outputs is for N = 1")
     if world > 1:
         import bench_multi
         res = bench_multi.headline_ranks(args, log)      # (None on ranks other than 0)

@@ -86,3 +86,31 @@ def test_under_torchrun_the_ranks_path_is_taken(monkeypatch, capsys):
     monkeypatch.setattr(bench_multi, "headline_ranks", lambda args, log: seen.append("ranks") or None)
     bench.main(["--gpus", "2", "--detail-out", ""])
     assert seen == ["ranks"] and capsys.readouterr().out == ""      # ranks other than 0 print nothing
+
+
+def test_a_plain_run_leaves_the_extras_to_full():
+    """Off by default: --full (the gate, roofline, other sections, CPU baseline) and --dump-outputs."""
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    b = bench.parse_args(["--full", "--no-deep", "--dump-outputs", "d"])
+    assert b.full and b.no_deep and b.dump_outputs == "d"
+
+
+def test_dumped_outputs_are_float_small_and_the_same_every_time(tmp_path):
+    """--dump-outputs on a block of the default size: float arrays, 64 MB at most, the same positions every run."""
+    import numpy as np
+    fs, frames = 640000, 128
+    iq = np.tile(np.array([[1, -2]], np.int16), (fs * frames, 1))      # the default block's size
+    iq[::7, 0] = 12345
+    iq[::11, 1] = -32768
+    for run in ("a", "b"):
+        bench.dump_outputs(iq, fs, str(tmp_path / run), lambda m: None)
+    total = 0
+    for name in ("iq_frame0", "iq_sample", "iq_sample_index"):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert total <= 64 << 20
+    idx = np.load(tmp_path / "a" / "iq_sample_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "iq_sample.npy"), iq[idx].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "iq_frame0.npy"), iq[:fs].astype(np.float32))

@@ -160,14 +160,15 @@ def test_bench_gpus_2_as_typed_runs_the_group_in_process():
 
 
 def test_bench_default_line_parses_and_carries_roofline_and_cpu_baseline():
-    """N = 1 as the driver runs it (short: 3 frames, 5 steps): one compact JSON line, last on stdout, with `roofline` and
-    `cpu_baseline`; the detail in the sidecar."""
+    """N = 1 with --full (short: 3 frames, 5 steps; the minutes-long sections left out): one compact JSON line, last on
+    stdout, with the parity gate, `roofline` and `cpu_baseline`; the detail in the sidecar."""
     import sys
     import tempfile
     require_ref(os.path.join(REF, "hacktv_ref"))
     with tempfile.TemporaryDirectory() as td:
         side = os.path.join(td, "detail.json")
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--frames", "3", "--settle", "0", "--detail-out", side]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--frames", "3", "--settle", "0", "--full", "--no-deep",
+               "--detail-out", side]
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT, env=env)
         assert r.returncode == 0, r.stdout.decode()[-2000:] + r.stderr.decode()[-3000:]
@@ -179,6 +180,28 @@ def test_bench_default_line_parses_and_carries_roofline_and_cpu_baseline():
     assert d["cpu_baseline"]["kind"] == "reference" and d["cpu_baseline"]["value"] > 0
     assert d["config"]["frames_per_gpu_per_step"] == 3
     assert "baseline_configs" in full and full["baseline_configs"]["4_secam_l_teletext_noaudio_device"]["secam_lines"]["host_frames"] == 0
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_rendered(golden, tmp_path):
+    """A plain N = 1 run: the line with the headline keys and nothing that --full adds; --dump-outputs writes the last
+    timed step's block -- frame 0 whole equals the reference's first frame, the sampled positions agree with it."""
+    import sys
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--frames", "3", "--settle", "0",
+           "--detail-out", "", "--dump-outputs", str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, cwd=ROOT, env=env)
+    assert r.returncode == 0, r.stdout.decode()[-2000:] + r.stderr.decode()[-3000:]
+    d = _last_line(r.stdout)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "Msamples/s" and d["dtype"] == "int16 data, int32 accumulate"
+    assert not {"parity_gate", "roofline", "cpu_baseline"} & set(d)
+    frame0, sample, idx = (np.load(out / (n + ".npy")) for n in ("iq_frame0", "iq_sample", "iq_sample_index"))
+    assert frame0.dtype == np.float32 and frame0.shape == (640000, 2)
+    assert sample.dtype == np.float32 and idx.dtype == np.float64 and sample.shape == (idx.size, 2)
+    assert util.sha256(frame0.astype(np.int16).tobytes()) == golden.cases["i_full"]["sha256_cumulative"][0]
+    first = idx < 640000
+    assert first.any() and np.array_equal(sample[first], frame0[idx[first].astype(np.int64)])
 
 
 def test_a_failure_of_the_c_group_leaves_the_harness_value_and_says_so():

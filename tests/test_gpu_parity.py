@@ -351,7 +351,7 @@ def test_late_frames_audio_is_additive_and_position_exact(golden):
     assert not diff.any()
 
 
-def test_dropin_binary_equals_reference_cli(golden):
+def test_dropin_binary_equals_reference_cli(golden, tmp_path):
     """the reference's own main(), av_test.c and rf_file.c, unmodified, linked
     with the video.h shim + libhvk (oracle/_ref/hacktv_hvk), must write the same bytes as the
     unmodified reference CLI. Compared through the committed digest of the reference's output
@@ -377,8 +377,9 @@ def test_dropin_binary_equals_reference_cli(golden):
         p.wait()
         return bytes(out)
 
-    util.passthru_signal().tofile("/tmp/hvk_passthru.bin")
-    util.rawbb_signal().tofile("/tmp/hvk_rawbb.bin")
+    passfile, rawfile = str(tmp_path / "hvk_passthru.bin"), str(tmp_path / "hvk_rawbb.bin")
+    util.passthru_signal().tofile(passfile)
+    util.rawbb_signal().tofile(rawfile)
     for case in ("i_full", "pal_bb", "m_full", "l_full", "l_tt", "i_swap_pass", "pal_fm_pass", "secam_fm_tail",
                  "i_px135", "pal_px135_s136", "i_vbi_tt", "m_vbi", "i_acp_cc", "ntsc_sv_f", "l_fid", "i_rawbb", "l_rawbb",
                  "i_rawbb_px16", "pal_rawbb_px135", "i_sis_filter", "ntsc_sv_f_px18", "i_pass_px135", "palm_full", "d_full", "ntsci_full", "pal60_bb", "palfm_f14", "palfm_f14_tail",
@@ -390,7 +391,7 @@ def test_dropin_binary_equals_reference_cli(golden):
         fs = c.get("frame_samples", c["width"] * c["lines"])
         bps = 2 if c["real"] else 4
         nframes = 3
-        flags = ["-m", c["mode"], "-s", str(c["sample_rate"])] + golden.cli_flags(case)
+        flags = ["-m", c["mode"], "-s", str(c["sample_rate"])] + golden.cli_flags(case, passfile, rawfile)
         ends = c.get("frame_ends") or [(n + 1) * fs for n in range(nframes)]       # (frames of two lengths: listed)
         if c["frames"] < nframes:
             nframes = c["frames"]

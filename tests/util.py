@@ -95,10 +95,16 @@ class Golden:
         lines += (list(range(9, 19)) + list(range(321, 331)) if x.get("acp") else []) + ([22] if x.get("cc608") else [])
         return tuple(sorted(set(l - 7 if l < 300 else 16 + l - 320 for l in lines)))
 
-    def cli_flags(self, case, passfile="/tmp/hvk_passthru.bin"):
-        """The reference CLI's flags for the case; passthru cases expect passthru_signal() at `passfile`."""
-        return [f.replace("@TTRAW@", os.path.join(GOLD, "ttraw.bin")).replace("@PASS@", passfile).replace("@RAWBB@", "/tmp/hvk_rawbb.bin")
-                for f in self.cases[case]["cli_flags"]]
+    def cli_flags(self, case, passfile=None, rawfile=None):
+        """The reference CLI's flags for the case; passthru cases expect passthru_signal() at `passfile`, raw
+        baseband cases rawbb_signal() at `rawfile` (both the caller's own files)."""
+        flags = [f.replace("@TTRAW@", os.path.join(GOLD, "ttraw.bin")) for f in self.cases[case]["cli_flags"]]
+        for mark, path in (("@PASS@", passfile), ("@RAWBB@", rawfile)):
+            if any(mark in f for f in flags):
+                if path is None:
+                    raise ValueError("case %s reads a file (%s): pass its path" % (case, mark))
+                flags = [f.replace(mark, path) for f in flags]
+        return flags
 
 
 def stream_bytes(iq, real):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/profile_round.sh TAG -- the measurement set kept under profiles/ (run on the GPU box via gpurun):
 #   gpurun --timeout 600 -- 'bash tools/profile_round.sh r01c'
-# 1. python bench.py (un-profiled; HIP-event kernel times, cpu_baseline)      -> gpurun_out/TAG/bench.json
+# 1. python bench.py --full --no-deep (un-profiled; HIP-event kernel times, cpu_baseline) -> $OUT/bench.json
 # 2. rocprofv3 --kernel-trace --stats of a short bench run                   -> gpurun_out/TAG/stats/
 # 3. four separate --pmc passes (never combined with trace domains other than
 #    --kernel-trace; TA_/TCP_ derived counters hang on this pool: not used)  -> gpurun_out/TAG/pmcN/
@@ -15,7 +15,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 BENCH="python $PWD/bench.py"
 
-timeout 900 $BENCH $BENCH_FLAGS --detail-out "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 $BENCH --full --no-deep $BENCH_FLAGS --detail-out "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"
 
 cd /tmp

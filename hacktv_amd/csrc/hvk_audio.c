@@ -1170,7 +1170,7 @@ static int _line_width(const hvk_audio_t *a, int64_t g)
 {
 	const hvk_kconst_t *k = &a->t->k;
 	if(k->rs_L == 0) return(k->width);
-	return((int) ((((g + 1) * k->width * k->rs_L + k->rs_D - 1) / k->rs_D) - ((g * k->width * k->rs_L + k->rs_D - 1) / k->rs_D)));
+	return((int) (hvk_tables_chunk_start(k, g + 1) - hvk_tables_chunk_start(k, g)));
 }
 
 /* Advance the stream by one line of W samples; carriers (W int16 pairs) receives the

@@ -1405,8 +1405,9 @@ extern "C" size_t hvk_audio_needed(const hvk_engine_t *e, int nframes)
 {
 	if(!e || !e->audio) return(0);
 	const hvk_kconst_t &k = e->t.k;
-	int64_t upto = _fstart(e, e->next_frame + nframes) + (int64_t) k.out_prime;
-	return(hvk_audio_source_needed(e->audio, upto));
+	int64_t upto = _fstart(e, e->next_frame + nframes);
+	if(upto < 0) return(0);
+	return(hvk_audio_source_needed(e->audio, upto + (int64_t) k.out_prime));
 }
 
 extern "C" int hvk_host_side_streams(hvk_engine_t *e, int64_t first, int64_t count,
@@ -1423,12 +1424,15 @@ extern "C" int hvk_host_sis_bursts(hvk_engine_t *e, int64_t first_line, int nlin
 	if(!e || !out || first_line < 0 || nlines < 0) return(HVK_ERROR);
 	if(!e->t.k.sis || !e->audio) return(HVK_UNSUPPORTED);
 	/* (where line first_line + nlines begins in the stream: behind the resampler emitted line j is chunk j + s, hvk_tables_frame_start()) */
-	int64_t upto = (first_line + nlines) * (int64_t) e->t.k.width;
+	int64_t upto;
+	if(__builtin_mul_overflow(first_line + nlines, (int64_t) e->t.k.width, &upto)) return(HVK_ERROR);
 	if(e->t.k.rs_L)
 	{
 		const hvk_kconst_t &k = e->t.k;
-		const int64_t s = 1 + (k.vf_type ? k.delay_lines : 0), g = first_line + nlines + s;
-		upto = (g * k.width * k.rs_L + k.rs_D - 1) / k.rs_D - (s * k.width * k.rs_L + k.rs_D - 1) / k.rs_D;
+		const int64_t s = 1 + (k.vf_type ? k.delay_lines : 0);
+		upto = hvk_tables_chunk_start(&k, first_line + nlines + s);
+		if(upto < 0) return(HVK_ERROR);
+		upto -= hvk_tables_chunk_start(&k, s);
 	}
 	int r = hvk_audio_advance(e->audio, upto);
 	if(r != HVK_OK) return(r);
@@ -1500,7 +1504,8 @@ extern "C" int hvk_secam_walk_stages(const hvk_engine_t *e, int64_t counts[3])
 extern "C" int64_t hvk_frame_start(const hvk_engine_t *e, int64_t frame)
 {
 	if(!e || frame < 0) return(HVK_ERROR);
-	return(_fstart(e, frame));
+	const int64_t v = _fstart(e, frame);
+	return(v < 0 ? HVK_ERROR : v);
 }
 
 extern "C" int hvk_secam_warmup_lines(hvk_engine_t *e)
@@ -1520,8 +1525,7 @@ extern "C" int hvk_passthru_write(hvk_engine_t *e, const int16_t *iq, size_t nsa
 extern "C" int hvk_line_widths(const hvk_engine_t *e, int64_t first_line, int nlines, int32_t *widths)
 {
 	if(!e || !widths || first_line < 0 || nlines < 0) return(HVK_ERROR);
-	hvk_tables_line_widths(&e->t, first_line, nlines, widths);
-	return(HVK_OK);
+	return(hvk_tables_line_widths(&e->t, first_line, nlines, widths));
 }
 
 extern "C" int hvk_host_offset_stream(hvk_engine_t *e, int64_t first, int64_t count, int16_t *out)

@@ -23,21 +23,28 @@ int hvk_e_sv_ring_records(hvk_engine *e, int64_t first_frame, int nframes)
 	 * after ev_staged of the stage before -- which this copy is in front of -- so a launch never reads another batch's
 	 * records, however far stage / launch / fetch calls are pipelined. */
 	const hvk_kconst_t &k = e->t.k;
-	const int64_t s = 1 + (k.vf_type ? k.delay_lines : 0), WL = (int64_t) k.width * k.rs_L, D = k.rs_D;
-	auto S = [&](int64_t j) { return(((j + s) * WL + D - 1) / D - (s * WL + D - 1) / D); };
-	auto width = [&](int64_t j) { return((int) (S(j + 1) - S(j))); };
-	const int wmax = e->t.max_width;
+	const int64_t s = 1 + (k.vf_type ? k.delay_lines : 0), D = k.rs_D, c_s = hvk_tables_chunk_start(&k, s);
+	const int64_t WL = (int64_t) k.width * k.rs_L, q = WL / D, r = WL % D;
+	/* (exact: hvk_e_stage() refused a batch whose end does not fit in int64) */
+	auto S = [&](int64_t j) { return(hvk_tables_chunk_start(&k, j + s) - c_s); };
 	/* (the luma stream lags the chunks by the first chunk the filter was fed and gave nothing for -- the last one dropped at
 	 * start-up: ITS width is what a content chunk's width is held against, the longer one or the shorter one as the rates have it) */
-	const int wref = s >= 1 ? width(-1) : wmax;
+	const int wref = (int) (c_s - hvk_tables_chunk_start(&k, s - 1));
 	const int64_t f0 = first_frame, j0 = f0 * k.lines, base = S(j0);
 	const long slab_in = (long) k.slab_lines * k.width;
 	const int nlines = nframes * k.lines;
+	int64_t Sp = S(j0 - 1), Sj = base, Sf = base;          /* where lines j - 1 and j begin, where line j's frame begins */
+	/* the line after, without a divide a line: with x = ceil(g W L / D) D - g W L in [0, D) (hvk_tables_chunk_residual()),
+	 * chunk g + 1 begins q + 1 samples after chunk g where r > x, q samples after it where not */
+	int64_t x = hvk_tables_chunk_residual(&k, j0 + s);
 
 	for(int i = 0; i < nlines; i++)
 	{
-		const int64_t j = j0 + i;
-		const int w = width(j), wp = j + s - 1 >= 0 ? width(j - 1) : wref, delta = wref - wp;       /* -1, 0 or 1 */
+		const int step = r > x;
+		const int64_t Sn = Sj + q + step;
+		x += step * D - r;
+		if(i % k.lines == 0) Sf = Sj;
+		const int w = (int) (Sn - Sj), wp = (int) (Sj - Sp), delta = wref - wp;       /* -1, 0 or 1 */
 		int kind = 0, src = 0;
 		if(w > wp)
 		{
@@ -45,7 +52,7 @@ int hvk_e_sv_ring_records(hvk_engine *e, int64_t first_frame, int nframes)
 			{
 				/* downwards: the raster's sub-carrier of the line before the content's, at the place the content ends */
 				const int y = i / k.lines;
-				const int64_t pl = S(j) - S((f0 + y) * k.lines);                    /* the line's first sample in its frame */
+				const int64_t pl = Sj - Sf;                                           /* the line's first sample in its frame */
 				const int64_t rr = pl + delta + k.rs_shift;
 				const int64_t n0 = (rr * D + e->h_frec[2 * y]) / k.rs_L;
 				const int64_t rho = n0 / k.width;
@@ -59,10 +66,12 @@ int hvk_e_sv_ring_records(hvk_engine *e, int64_t first_frame, int nframes)
 				kind = 3;
 			}
 		}
-		e->h_svrec[4 * i + 0] = (int) (S(j) - base);
+		e->h_svrec[4 * i + 0] = (int) (Sj - base);
 		e->h_svrec[4 * i + 1] = w | ((delta & 15) << 16) | (kind << 20);
 		e->h_svrec[4 * i + 2] = src;
 		e->h_svrec[4 * i + 3] = 0;
+		Sp = Sj;
+		Sj = Sn;
 	}
 	HIPCHK(hipMemcpyAsync(e->d_svrec, e->h_svrec, (size_t) nlines * 16, hipMemcpyHostToDevice, e->stream));
 	return(HVK_OK);

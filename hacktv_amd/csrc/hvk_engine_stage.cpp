@@ -709,6 +709,13 @@ int hvk_e_stage(hvk_engine_t *e, int64_t first_frame, int64_t stride, int nframe
 		if(slots && (slots[i] < 0 || slots[i] >= e->frame_slots)) return(HVK_ERROR);
 	}
 	if(e->t.k.rs_irr && stride != 1) return(HVK_UNSUPPORTED);        /* frames of two lengths: a batch is one run of samples */
+	{
+		/* positions in the stream are exact while they fit in int64 (hvk_tables_chunk_start()): past that, refused -- the end of the
+		 * last frame staged is the furthest any record of the batch reaches */
+		int64_t last;
+		if(__builtin_mul_overflow((int64_t) (nframes - 1), stride, &last) || __builtin_add_overflow(last, first_frame + 1, &last) ||
+		   _fstart(e, last) < 0) return(HVK_UNSUPPORTED);
+	}
 	/* (... whose NICAM symbol starts are kept as 29-bit offsets from its first sample: checked here, before any chain has moved) */
 	if(e->t.k.rs_irr && e->audio && (_fstart(e, first_frame + nframes) - _fstart(e, first_frame)) * 8 >= 0x7FFFFFFF) return(HVK_UNSUPPORTED);
 	if(e->secam && (stride != 1 || first_frame != e->secam_next)) return(HVK_UNSUPPORTED);   /* one serial chain over the whole stream (hvk_secam.c): frames in order, no gaps */
@@ -905,8 +912,10 @@ int hvk_e_stage(hvk_engine_t *e, int64_t first_frame, int64_t stride, int nframe
 		const size_t foff = k.rs_irr ? (size_t) (fpos - _fstart(e, first_frame)) : (size_t) i * FS;
 		if(k.rs_irr)
 		{
-			/* hvk_k_resample: c = B D - f RS L, and the frame's place in the batch's run */
-			e->h_frec[2 * i + 0] = (int) (fpos * k.rs_D - f->frame_index * (int64_t) k.raster_samples * k.rs_L);
+			/* hvk_k_resample: c = B D - f RS L, and the frame's place in the batch's run. B = ceil(g W L / D) - ceil(s W L / D) with
+			 * g = f lines + s and RS L = lines W L, so c is the difference of the two chunks' residuals -- no large product */
+			const int64_t s = 1 + (k.vf_type ? k.delay_lines : 0);
+			e->h_frec[2 * i + 0] = (int) (hvk_tables_chunk_residual(&k, f->frame_index * k.lines + s) - hvk_tables_chunk_residual(&k, s));
 			e->h_frec[2 * i + 1] = (int) foff;
 		}
 

@@ -223,8 +223,12 @@ typedef struct {
 
 int hvk_tables_build(hvk_tables_t *t, const hvk_config_t *conf, unsigned int sample_rate, unsigned int pixel_rate);
 /* widths of output lines [first, first + n) of the stream (they vary with the resampler) */
-void hvk_tables_line_widths(const hvk_tables_t *t, int64_t first, int n, int32_t *widths);
-int64_t hvk_tables_frame_start(const hvk_tables_t *t, int64_t frame);     /* first output sample of a frame, counted from the stream's first */
+int hvk_tables_line_widths(const hvk_tables_t *t, int64_t first, int n, int32_t *widths);      /* HVK_ERROR past the exact domain */
+int64_t hvk_tables_frame_start(const hvk_tables_t *t, int64_t frame);     /* first output sample of a frame, counted from the stream's first; -1 where it does not fit */
+/* behind the resampler: where chunk g begins, ceil(g W L / D) (-1 where it does not fit in int64), and ceil(g W L / D) D - g W L --
+ * the one place positions in the resampled stream are worked out */
+int64_t hvk_tables_chunk_start(const hvk_kconst_t *k, int64_t g);
+int64_t hvk_tables_chunk_residual(const hvk_kconst_t *k, int64_t g);
 void hvk_tables_free(hvk_tables_t *t);
 void hvk_tables_default_ghost(hvk_tables_t *t);
 long hvk_tables_get(const hvk_tables_t *t, const char *name, void *dst, long max_bytes);

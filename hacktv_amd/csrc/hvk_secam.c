@@ -306,8 +306,9 @@ int hvk_secam_frame(hvk_secam_t *s, int64_t frame_index, const uint32_t *fb1, in
 		{
 			const hvk_secam_task_t *q = &T[i - nprime];
 			const int line = q->line;
-			const int dr = ((frame * s->lines) + line) & 1;
-			const int pdr = ((frame * s->lines) + q->prev_line) & 1;
+			/* (frame * lines + line as the reference's int: wrapped in unsigned, hvk_secam.hip) */
+			const int dr = (int) ((unsigned) frame * (unsigned) s->lines + (unsigned) line) & 1;
+			const int pdr = (int) ((unsigned) frame * (unsigned) s->lines + (unsigned) q->prev_line) & 1;
 			/* the frame the line's field shows */
 			const int second = k->fields == 2 && line >= k->hline;
 			const uint32_t *fb = second ? fb2 : fb1;
@@ -338,9 +339,9 @@ int hvk_secam_frame(hvk_secam_t *s, int64_t frame_index, const uint32_t *fb1, in
 	/* ---- the serial part ---- */
 #define TASK_ARGS(i) \
 	const int line_ = (i) < nprime ? 0 : T[(i) - nprime].line; \
-	const int dr_ = ((frame * s->lines) + line_) & 1; \
+	const int dr_ = (int) ((unsigned) frame * (unsigned) s->lines + (unsigned) line_) & 1; \
 	const int sr_ = (i) < nprime ? k->burst_left + k->burst_width : T[(i) - nprime].sr; \
-	const int pos_ = ((frame * s->lines) + line_) % 3 == 0; \
+	const int pos_ = (int) ((unsigned) frame * (unsigned) s->lines + (unsigned) line_) % 3 == 0; \
 	const int clear_ = (i) >= nprime && (T[(i) - nprime].flags & HVK_SECAM_TASK_CLEAR)
 #define TASK_RUN(i, st, o) \
 	do { \

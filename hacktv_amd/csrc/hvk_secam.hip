@@ -95,8 +95,9 @@ __device__ __forceinline__ task_view task_of(const hvk_secam_args_t &a, const in
 		v.fid = (q.flags & HVK_SECAM_TASK_FID) != 0;
 	}
 	{
-		/* (frame * lines + line) as the reference's int */
-		const int n = (int) v.fnum * a.lines + v.line;
+		/* (frame * lines + line) as the reference's int, the wrap past 2^31 its build makes (two's complement) done in unsigned:
+		 * defined here, the same bits */
+		const int n = (int) ((unsigned) v.fnum * (unsigned) a.lines + (unsigned) v.line);
 		v.dr = n & 1;
 		v.phase_pos = n % 3 == 0;
 	}
@@ -190,7 +191,7 @@ void hvk_k_secam_cells(const hvk_secam_args_t a)
 			}
 			have_prev = v.prev_line != 0;
 			{
-				const int pn = (int) v.fnum * a.lines + v.prev_line;
+				const int pn = (int) ((unsigned) v.fnum * (unsigned) a.lines + (unsigned) v.prev_line);
 				pcomp = (pn & 1) ? 0 : 1;
 			}
 			if(have_prev)

@@ -1902,37 +1902,68 @@ void hvk_tables_free(hvk_tables_t *t)
 	memset(t, 0, sizeof(*t));
 }
 
+/* Where resampler chunk g -- the outputs made from raster line g, g >= 0 -- begins in the resampled stream: ceil(g W L / D),
+ * exact wherever that fits in int64, -1 where it does not. With g = a D + b and W L = q D + r,
+ * ceil(g W L / D) = a W L + b q + ceil(b r / D): b q < W L and b r < D^2, so a W L is the only product that can leave 64 bits. */
+int64_t hvk_tables_chunk_start(const hvk_kconst_t *k, int64_t g)
+{
+	const int64_t WL = (int64_t) k->width * k->rs_L, D = k->rs_D;
+	const int64_t a = g / D, b = g % D, q = WL / D, r = WL % D;
+	int64_t v;
+	if(g < 0) return(-1);
+	if(__builtin_mul_overflow(a, WL, &v) || __builtin_add_overflow(v, b * q + (b * r + D - 1) / D, &v)) return(-1);
+	return(v);
+}
+
+/* ceil(g W L / D) D - g W L, in [0, D): what the chunk's first output sample lies past raster position g W / D, in 1 / (L D)
+ * of a raster sample -- ceil(b r / D) D - b r with b and r as above; no large product, for every g >= 0 */
+int64_t hvk_tables_chunk_residual(const hvk_kconst_t *k, int64_t g)
+{
+	const int64_t D = k->rs_D, br = (g % D) * (((int64_t) k->width * k->rs_L) % D);
+	return((D - br % D) % D);
+}
+
 int64_t hvk_tables_frame_start(const hvk_tables_t *t, int64_t frame)
 {
 	const hvk_kconst_t *k = &t->k;
-	if(!k->rs_irr) return(frame * (int64_t) k->frame_samples);
+	int64_t v;
+	if(frame < 0) return(-1);
+	if(!k->rs_L) return(__builtin_mul_overflow(frame, (int64_t) k->frame_samples, &v) ? -1 : v);
 	/* where the frame's first EMITTED line begins (hvk_tables_line_widths(): emitted line j is the resampler's chunk
-	 * j + s, chunk g begins at ceil(g W L / D)) */
+	 * j + s) -- frame * frame_samples where frames are all of one length, the same number */
 	{
 		const int64_t s = 1 + (k->vf_type ? k->delay_lines : 0);
-		const int64_t g = frame * k->lines + s;
-		return((g * k->width * k->rs_L + k->rs_D - 1) / k->rs_D - (s * k->width * k->rs_L + k->rs_D - 1) / k->rs_D);
+		if(__builtin_mul_overflow(frame, (int64_t) k->lines, &v) || __builtin_add_overflow(v, s, &v)) return(-1);
+		v = hvk_tables_chunk_start(k, v);
+		return(v < 0 ? -1 : v - hvk_tables_chunk_start(k, s));
 	}
 }
 
-void hvk_tables_line_widths(const hvk_tables_t *t, int64_t first, int n, int32_t *widths)
+int hvk_tables_line_widths(const hvk_tables_t *t, int64_t first, int n, int32_t *widths)
 {
 	const hvk_kconst_t *k = &t->k;
+	const int64_t s = 1 + (k->vf_type ? k->delay_lines : 0);
+	int64_t g, lo;
 	int i;
 
+	if(first < 0 || n < 0) return(HVK_ERROR);
+	if(k->rs_L == 0)
+	{
+		for(i = 0; i < n; i++) widths[i] = k->width;
+		return(HVK_OK);
+	}
+	/* emitted line j is resampler chunk j + (chunks dropped at start-up); chunk g holds the outputs made from raster line g:
+	 * [ceil(g W L / D), ceil((g + 1) W L / D)). Exact, or nothing written: the end of the last line has to fit. */
+	if(__builtin_add_overflow(first, (int64_t) n + s, &g) || hvk_tables_chunk_start(k, g) < 0) return(HVK_ERROR);
+	g = first + s;
+	lo = hvk_tables_chunk_start(k, g);
 	for(i = 0; i < n; i++)
 	{
-		if(k->rs_L == 0) widths[i] = k->width;
-		else
-		{
-			/* emitted line j is resampler chunk j + (chunks dropped at start-up); chunk g holds the
-			 * outputs made from raster line g: [ceil(g W L / D), ceil((g + 1) W L / D)) */
-			const int64_t g = first + i + 1 + (k->vf_type ? k->delay_lines : 0);
-			const int64_t lo = (g * k->width * k->rs_L + k->rs_D - 1) / k->rs_D;
-			const int64_t hi = ((g + 1) * k->width * k->rs_L + k->rs_D - 1) / k->rs_D;
-			widths[i] = (int32_t) (hi - lo);
-		}
+		const int64_t hi = hvk_tables_chunk_start(k, g + i + 1);
+		widths[i] = (int32_t) (hi - lo);
+		lo = hi;
 	}
+	return(HVK_OK);
 }
 
 static long _give(void *dst, long max_bytes, const void *src, long bytes)

@@ -121,7 +121,8 @@ int hvk_open_rates(hvk_engine_t **e, const hvk_config_t *conf, unsigned int samp
                    int device, int max_frames);
 
 /* Widths of output lines [first_line, first_line + nlines) of the stream, counted from 0 (what
- * vid_next_line() puts in vid_line_t.width): always info.width without the resampler. */
+ * vid_next_line() puts in vid_line_t.width): always info.width without the resampler. Exact wherever the end of the
+ * last line, as a sample position, fits in int64; past that HVK_ERROR and nothing is written. */
 int hvk_line_widths(const hvk_engine_t *e, int64_t first_line, int nlines, int32_t *widths);
 
 /* The first output sample of stream frame `frame`, counted from the stream's first: frame * frame_samples -- but for
@@ -129,7 +130,9 @@ int hvk_line_widths(const hvk_engine_t *e, int64_t first_line, int nlines, int32
  * 450450 * 32 / 27). Frames then have two lengths one sample apart, hvk_info_t.frame_samples is the longer, a render of n
  * frames from frame f yields hvk_frame_start(f + n) - hvk_frame_start(f) samples without gaps (what hvk_fetch() counts
  * in), and such a stream renders in order on one engine: no strides, no interleaved output slots. The lines keep the
- * widths hvk_line_widths() gives (src/video.c:3246): they never depended on where a frame is cut. */
+ * widths hvk_line_widths() gives (src/video.c:3246): they never depended on where a frame is cut. Exact wherever the
+ * frame's first sample fits in int64 (behind the resampler: its first line's chunk, ceil(g W L / D)); HVK_ERROR (negative)
+ * past that, never a wrapped number. */
 int64_t hvk_frame_start(const hvk_engine_t *e, int64_t frame);
 
 /* vid_free(): src/video.c:4706 */
@@ -267,6 +270,8 @@ int hvk_render_strided(hvk_engine_t *e, int64_t first_frame, int64_t stride, int
  * the last one ended, does not have the frame before: on those modes it is refused with HVK_UNSUPPORTED --
  * hvk_stage_strided_prev() takes the slot that holds the frame before, the frame's own slot where the
  * picture does not change.) */
+/* (A batch reaching past the last frame whose end, as a sample position, fits in int64 is refused with HVK_UNSUPPORTED before
+ * anything moves: hvk_frame_start().) */
 int hvk_stage_strided(hvk_engine_t *e, int64_t first_frame, int64_t stride, int nframes, const int32_t *slots);
 /* As hvk_stage_strided(), for sharded streams whose pictures change: prev_slots[i] names the frame slot that holds the
  * picture of the frame BEFORE staged frame i (with conf.interlace: the one its second field shows), -1 if the caller

@@ -138,6 +138,16 @@ void orc_sis_free(orc_t *s)
 	s->sis_blank_win = NULL;
 }
 
+/* ceil(g width L / D), the first sample of the resampler's chunk g, without the product g width L: with g = a D + b and
+ * width L = q D + r it is a width L + b q + ceil(b r / D), b q < width L, b r < D^2 (the caller's positions keep a width L in
+ * 64 bits) */
+static long long _chunk_start(const orc_t *s, long long g)
+{
+	const long long WL = (long long) s->width * s->rs_L, D = s->rs_D;
+	const long long a = g / D, b = g % D;
+	return(a * WL + b * (WL / D) + (b * (WL % D) + D - 1) / D);
+}
+
 /* The block the audio thread has handed over by the time invocation `call` (counted from 1) encodes a frame: block j
  * is complete with tick 32 (j + 1), which fires on stream sample ceil(32 (j + 1) * rate / 32000) - 1
  * (src/video.c:3273-3276); the audio thread has `call - 1` whole lines behind it and `visible` samples of this step's.
@@ -147,7 +157,7 @@ static int _block_seen(orc_t *s, long call, int16_t out[64])
 	const int visible = s->sis_visible;
 	/* samples [0, reach) are behind the audio thread: call - 1 of its lines -- behind the resampler those are the resampler's
 	 * chunks, chunk g beginning at ceil(g width L / D) (src/video.c:3627-3651) */
-	const long long reach = (s->rs_taps ? ((long long) (call - 1) * s->width * s->rs_L + s->rs_D - 1) / s->rs_D : (long long) (call - 1) * s->width) + visible;
+	const long long reach = (s->rs_taps ? _chunk_start(s, call - 1) : (long long) (call - 1) * s->width) + visible;
 	long long j, n;
 	int i;
 
